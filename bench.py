@@ -9,9 +9,16 @@ of the hot path over the batch: reset, the engine's feed (k_part +
 k_bucket_count + k_pair_fold + the statistics kernels for 8 <= k <= 12) and
 fk_engine_finish.
 
-The same line carries the north-star gate as a sub-record ("north_star"):
-k=6 over a 10 G-base pure-ACGT genome (1.5-Gbase chromosomes), with its own
-value, ms_per_step and roofline (k_count).
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what that
+headline needs: it makes the input, warms up, times the N steps, writes the
+last step's outputs when --dump-outputs DIR is given, and prints the line.
+Everything else the bench measures or checks runs only with --full: the
+"north_star" and "weak_scaling" sub-records, both CPU baselines and
+--verify-single.
+
+--full: the same line carries the north-star gate as a sub-record
+("north_star"): k=6 over a 10 G-base pure-ACGT genome (1.5-Gbase
+chromosomes), with its own value, ms_per_step and roofline (k_count).
 
 With --gpus N (one process per GPU, torch.distributed over RCCL; without a
 launcher `python bench.py --gpus N` starts torch.distributed.run itself as a
@@ -19,12 +26,12 @@ child process) the headline is BASELINE.json configs[3]: the same 10 G-base
 genome cut into N shards (strong scaling).  Each shard's entry state is
 stitched and the count tables merged inside the library
 (findkmer_amd/dist.py, fk_engine_shard_exchange) -- the path's real exchange
-steps.  A "weak_scaling" sub-record gives every rank a whole 10 G-base shard
+steps.  With --full a "weak_scaling" sub-record gives every rank a whole 10 G-base shard
 of an N x 10 G-base stream.
 
 Prints ONE JSON line on rank 0 (contract in the task statement): value =
 bases/s over all ranks, "roofline" for the dominant kernel (HIP events on the
-engine's stream, recorded inside the launch), "cpu_baseline" (the reference
+engine's stream, recorded inside the launch) and, with --full, "cpu_baseline" (the reference
 binary on a bounded sample, rank 0 at N=1 only) and "cpu_baseline_multicore"
 (the oracle's dense scan over 16 host threads, the "fast CPU" of BASELINE.md).
 """
@@ -51,19 +58,25 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beyond the headline: the north-star and weak-scaling sub-records, "
+                         "the CPU baselines, --verify-single (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed to DIR/<name>.npy "
+                         "(float64; see dump_outputs)")
     ap.add_argument("--k", type=int, default=11)
     ap.add_argument("--bases", type=int, default=10_000_000_000,
                     help="bases of the headline stream, split over the --gpus ranks (strong scaling)")
     ap.add_argument("--weak-bases", type=int, default=10_000_000_000,
-                    help="N > 1 sub-record: this many bases per GPU (weak scaling; 0 = skip)")
+                    help="--full, N > 1 sub-record: this many bases per GPU (weak scaling; 0 = skip)")
     ap.add_argument("--fasta-line", type=int, default=80, help="80 = FASTA (configs[2]); 0 = pure ACGT stream")
     ap.add_argument("--seed", type=int, default=2)
     ap.add_argument("--chrom", type=int, default=CHROM,
                     help="an 'N' run break at every base index that is a multiple of this (0 = one run)")
     ap.add_argument("--north-star-bases", type=int, default=10_000_000_000,
-                    help="sub-record: k=6 over this many pure-ACGT bases per GPU (0 = skip)")
+                    help="--full sub-record: k=6 over this many pure-ACGT bases per GPU (0 = skip)")
     ap.add_argument("--cpu-sample-bytes", type=int, default=0, help="0 = auto (~10-20 s of reference CPU work)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without its CPU baselines")
     ap.add_argument("--timing-every", type=int, default=4,
                     help="time the count kernel with HIP events on every Nth step")
     ap.add_argument("--stitched", action="store_true",
@@ -74,8 +87,13 @@ def parse(argv=None):
                     help="nccl = RCCL over xGMI (one GPU per rank); gloo = host-side rehearsal")
     ap.add_argument("--verify-single", action="store_true",
                     help="rank 0 also counts the whole stream with one engine and compares the merged "
-                         "table and counters with it (configs[3] parity)")
-    return ap.parse_args(argv)
+                         "table and counters with it (configs[3] parity; needs --full)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.verify_single and not args.full:
+        ap.error("--verify-single is a check beyond the headline: run it with --full")
+    return args
 
 
 # ---------------------------------------------------------------- the stream
@@ -205,9 +223,10 @@ class Ctx:
             args, world, rank, local, dist, coll_dev
 
 
-def measure(ctx, k, n, L, seed, chrom, steps, warmup, verify=False):
+def measure(ctx, k, n, L, seed, chrom, steps, warmup, verify=False, dump=None):
     """Time `steps` passes of the hot path over this rank's shard of the
-    stream (n bases per rank).  Returns the record (rank 0's view)."""
+    stream (n bases per rank).  Returns the record (rank 0's view).  dump: a
+    directory for the last step's outputs (dump_outputs, rank 0)."""
     import torch
     import findkmer_amd as fk
     import findkmer_amd.dist as fkdist
@@ -280,6 +299,9 @@ def measure(ctx, k, n, L, seed, chrom, steps, warmup, verify=False):
         want = expected_windows(world * n, k, chrom if chrom_on else 0)
         assert total == want, (total, want)
 
+    if dump and rank == 0:
+        dump_outputs(dump, k, eng, last, merged)
+
     # what RCCL itself reports for the communicator the exchange ran on, from
     # every rank: the world the line claims is the world that ran
     rccl = None
@@ -331,6 +353,75 @@ def measure(ctx, k, n, L, seed, chrom, steps, warmup, verify=False):
     del buf, merge_t
     torch.cuda.empty_cache()
     return rec
+
+
+DUMP_WHOLE = 1 << 22     # a table of up to this many bins is dumped whole (32 MB as float64)
+DUMP_WINDOWS = 32        # else this many windows of DUMP_WINDOW bins each, at starts drawn from DUMP_SEED
+DUMP_WINDOW = 1 << 16
+DUMP_SEED = 20
+DUMP_COUNTERS = ("windows", "valid_bases", "base_count", "depth1", "distinct", "unknown_chars", "scanned_bytes",
+                 "hit_eof_byte", "unterminated_header")
+
+
+def dump_windows(lo, hi, nbins):
+    """The bin ranges [start, start + n) of the part [lo, hi) of an
+    nbins-bin table that dump_outputs writes: a whole table of up to
+    DUMP_WHOLE bins (k <= 11; written without an index), a part of up to
+    DUMP_WINDOWS * DUMP_WINDOW bins whole, else DUMP_WINDOWS windows at fixed
+    pseudo-random starts (the same for every run and build)."""
+    import numpy as np
+    if ((lo, hi) == (0, nbins) and nbins <= DUMP_WHOLE) or hi - lo <= DUMP_WINDOWS * DUMP_WINDOW:
+        return [(lo, hi - lo)]
+    rng = np.random.default_rng(DUMP_SEED)
+    return [(lo + int(s), DUMP_WINDOW) for s in sorted(rng.integers(0, hi - lo - DUMP_WINDOW, DUMP_WINDOWS).tolist())]
+
+
+def dump_outputs(path, k, eng, last, merged):
+    """--dump-outputs: what the last timed step computed, as a caller of the
+    path receives it, into path/<name>.npy (float64: u32 counts, u64 counters
+    and bin indices below 2^40 are exact), under 64 MB in all:
+
+      counters.npy     DUMP_COUNTERS in that order (base_count and depth1 four
+                       values each) of the fk_result, or of the merged result
+                       of a sharded pass
+      table.npy        the count table: every bin for k <= 11; for 12 <= k <= 16
+                       the bins of dump_windows() side by side; for k >= 17 the
+                       counts of the distinct k-mers whose index lies in those
+                       windows.  A sharded pass dumps from the part of the
+                       merged table that rank 0 holds.
+      table_index.npy  (k >= 12) the bin index of every table.npy entry
+    """
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    res = merged if merged is not None else last
+    vals = []
+    for name in DUMP_COUNTERS:
+        v = getattr(res, name)
+        vals += [int(x) for x in v] if name in ("base_count", "depth1") else [int(v)]
+    np.save(os.path.join(path, "counters.npy"), np.array(vals, dtype=np.float64))
+
+    lo, hi = (merged.lo, merged.hi) if merged is not None else (0, 1 << (2 * k))
+    wins = dump_windows(lo, hi, 1 << (2 * k))
+    index, counts = [], []
+    for start, n in wins:
+        if k > 16:      # sparse table: the runs with keys in the window
+            if merged is not None:
+                a, b = np.searchsorted(merged.keys, np.array([start, start + n], dtype=np.uint64))
+                keys, cnts = merged.keys[a:b], merged.counts[a:b]
+            else:
+                keys, cnts = eng.sparse_range(start, start + n)
+            index.append(keys.astype(np.float64))
+            counts.append(cnts.astype(np.float64))
+            continue
+        if merged is not None:
+            t = merged.table[start - lo:start - lo + n].cpu().numpy().view(np.uint32)
+        else:
+            t = eng.table() if n == 1 << (2 * k) else eng.table_range(start, n)
+        index.append(np.arange(start, start + n, dtype=np.float64))
+        counts.append(t.astype(np.float64))
+    np.save(os.path.join(path, "table.npy"), np.concatenate(counts))
+    if k > 11:
+        np.save(os.path.join(path, "table_index.npy"), np.concatenate(index))
 
 
 def traffic_for(k, L, nbytes, main, what="hbm_bytes_per_launch"):
@@ -455,18 +546,20 @@ def main():
     # configs[2] split N ways, counted by N ranks, merged)
     n = shard_bases(args.bases, world, args.fasta_line)
     head = measure(ctx, args.k, n, args.fasta_line, args.seed, args.chrom, args.steps, args.warmup,
-                   verify=args.verify_single)
+                   verify=args.verify_single, dump=args.dump_outputs)
     if head.get("transport") == "rccl-native":
         # the world this line claims is the world RCCL itself reports
         assert head["rccl"]["nranks"] == world, (head["rccl"], world)
+    # everything from here to the line itself is --full's: a plain run has
+    # its headline and prints it
     weak = None
-    if world > 1 and args.weak_bases > 0:
+    if args.full and world > 1 and args.weak_bases > 0:
         # sub-record: every rank a whole `weak_bases` shard of an N x as long
         # stream (per-GPU work fixed as N grows)
         weak = measure(ctx, args.k, shard_bases(args.weak_bases, 1, args.fasta_line), args.fasta_line, args.seed,
                        args.chrom, args.steps, args.warmup)
     ns = None
-    if args.north_star_bases > 0:
+    if args.full and args.north_star_bases > 0:
         ns = measure(ctx, 6, args.north_star_bases, 0, 1, CHROM, args.steps, args.warmup)
         ns["gate"] = "k=6 over a 10 GB synthetic genome at >= 70% of single-GPU HBM-read roofline (BASELINE.json)"
 
@@ -507,7 +600,7 @@ def main():
     if ns is not None:
         out["north_star"] = {key: ns[key] for key in ("workload", "gate", "value", "ms_per_step", "roofline",
                                                        "exchange", "transport") if key in ns}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # ~15 s of reference CPU work: ~76 Mbases/s at k=6, ~3 Mbases/s at k=11
         sample = args.cpu_sample_bytes or (1 << 30 if args.k <= 7 else 48 << 20)
         sample = min(sample, args.bases)

@@ -5,8 +5,8 @@ set -o pipefail
 cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 mkdir -p gpurun_out
-timeout -k 10 300 python bench.py > gpurun_out/r06b_bench.json 2> gpurun_out/r06b_bench.err || { tail -20 gpurun_out/r06b_bench.err; exit 1; }
-tail -1 gpurun_out/r06b_bench.json | cut -c1-200
+timeout -k 10 300 python bench.py --full > $TMPDIR/r06b_bench.json 2> $TMPDIR/r06b_bench.err || { tail -20 $TMPDIR/r06b_bench.err; exit 1; }
+tail -1 $TMPDIR/r06b_bench.json | cut -c1-200
 OUT=gpurun_out/r06b_k15 K=15 BASES=1000000000 TRACE_ONLY=1 bash scripts/gpu_profile.sh || exit 1
 OUT=gpurun_out/r06b_k16 K=16 BASES=1000000000 bash scripts/gpu_profile.sh || exit 1
 for k in 17 18 20; do

@@ -6,8 +6,8 @@ cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 mkdir -p gpurun_out
 bash scripts/gpu_suite.sh || exit 1
-timeout -k 10 300 python bench.py > gpurun_out/r06d_bench.json 2> gpurun_out/r06d_bench.err || { tail -20 gpurun_out/r06d_bench.err; exit 1; }
-tail -1 gpurun_out/r06d_bench.json | cut -c1-200
+timeout -k 10 300 python bench.py --full > $TMPDIR/r06d_bench.json 2> $TMPDIR/r06d_bench.err || { tail -20 $TMPDIR/r06d_bench.err; exit 1; }
+tail -1 $TMPDIR/r06d_bench.json | cut -c1-200
 for k in 15 16; do
   OUT=gpurun_out/r06d_k$k K=$k BASES=1000000000 TRACE_ONLY=1 bash scripts/gpu_profile.sh || exit 1
 done

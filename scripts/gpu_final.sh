@@ -6,8 +6,8 @@ set -o pipefail
 cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 mkdir -p gpurun_out
-timeout -k 10 300 python bench.py > gpurun_out/bench_final.json 2> gpurun_out/bench_final.err || { tail -20 gpurun_out/bench_final.err; exit 1; }
-tail -1 gpurun_out/bench_final.json | cut -c1-300
+timeout -k 10 300 python bench.py --full > $TMPDIR/bench_final.json 2> $TMPDIR/bench_final.err || { tail -20 $TMPDIR/bench_final.err; exit 1; }
+tail -1 $TMPDIR/bench_final.json | cut -c1-300
 OUT=gpurun_out/prof_k11 bash scripts/gpu_profile.sh || exit 1
 OUT=gpurun_out/prof_k6 K=6 L=0 SEED=1 bash scripts/gpu_profile.sh || exit 1
 for k in 12 13 14 15 16; do

@@ -6,6 +6,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 import bench
 from conftest import REPO
 
@@ -27,6 +29,31 @@ def test_world_mismatch_refused_before_torch():
                        cwd=REPO, env=env, capture_output=True, text=True, timeout=60)
     assert p.returncode == 2, p.stderr
     assert "WORLD_SIZE=2 but --gpus 8" in p.stderr
+
+
+def test_plain_run_is_the_default_and_full_is_an_option():
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    a = bench.parse(["--full", "--verify-single", "--dump-outputs", "d"])
+    assert a.full and a.verify_single and a.dump_outputs == "d"
+    # a check beyond the headline without --full, or no timed step: refused
+    for argv in (["--verify-single"], ["--steps", "0"]):
+        with pytest.raises(SystemExit) as ei:
+            bench.parse(argv)
+        assert ei.value.code == 2
+
+
+def test_dump_windows_are_fixed_and_bounded():
+    assert bench.dump_windows(0, 1 << 22, 1 << 22) == [(0, 1 << 22)]           # k = 11: the whole table
+    assert bench.dump_windows(1 << 21, 1 << 22, 1 << 24) == [(1 << 21, 1 << 21)]  # a rank's small slice
+    for lo, hi in ((0, 1 << 24), (0, 1 << 40), (3 << 30, 1 << 32), (1 << 22, 1 << 23)):
+        w = bench.dump_windows(lo, hi, 1 << 40)
+        assert w == bench.dump_windows(lo, hi, 1 << 40) == sorted(w)     # the same sample every run
+        assert len(w) == bench.DUMP_WINDOWS
+        assert all(lo <= s and s + n <= hi and n == bench.DUMP_WINDOW for s, n in w)
+    # table.npy + table_index.npy as float64, with counters.npy: under 64 MB
+    assert 2 * 8 * bench.DUMP_WINDOWS * bench.DUMP_WINDOW + 8 * 32 < 64_000_000
+    assert 8 * bench.DUMP_WHOLE + 8 * 32 < 64_000_000
 
 
 def test_launcher_command():

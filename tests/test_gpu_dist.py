@@ -61,7 +61,7 @@ def test_bench_gpus_flag_launches_the_ranks():
     bench starts torch.distributed.run itself as a child process, two ranks
     count the two halves of one stream (strong scaling), and the merged-count
     guard holds; the weak sub-record gives each rank a whole shard"""
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--dist-backend", "gloo",
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--full",
            "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--north-star-bases", "0",
            "--k", "11", "--fasta-line", "80", "--bases", "25600000", "--weak-bases", "12800000",
            "--chrom", "20000000"]
@@ -86,7 +86,7 @@ def test_configs3_eight_ranks_full_size():
     out = _torchrun(8, 29690, os.path.join(REPO, "bench.py"),
                     ["--gpus", "8", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--dist-backend", "gloo",
                      "--north-star-bases", "0", "--k", "11", "--fasta-line", "80", "--bases", "10000000000",
-                     "--weak-bases", "0", "--verify-single"])
+                     "--weak-bases", "0", "--full", "--verify-single"])
     assert out["n_gpus"] == 8 and out["exchange"] == "stitched"
     assert out["scaling"] == "strong" and out["config"]["total_bases"] == 10_000_000_000
     assert out["config"]["bases_per_gpu"] == 1_250_000_000
