@@ -887,8 +887,10 @@ int sp_grow(fk_engine *e, void **buf, uint64_t *cap, uint64_t used, uint64_t nee
 int sp_retain(fk_engine *e, const uint8_t *dbuf, uint64_t len, const Geo &g) {
     /* borrowed (opts.borrow_input, a 16-B aligned device feed): finish reads
        the caller's bytes again; no copy (a 10 GB feed: 4.4 ms of a k = 17
-       step) */
-    const bool borrow = e->seg_borrow && ((uintptr_t)dbuf & 15) == 0;
+       step).  Not a segment process_segment moved into the staging buffer
+       (a borrowed feed's last segment, shorter than a lane): the next staged
+       feed overwrites those bytes, so they are copied like any staged feed */
+    const bool borrow = e->seg_borrow && ((uintptr_t)dbuf & 15) == 0 && dbuf != e->d_stage;
     int rc = borrow ? FK_OK : sp_grow(e, (void **)&e->d_keep, &e->keep_cap, e->keep_len, e->keep_len + len + 16);
     if (rc) return rc;
     const uint64_t sb = g.nranges * sizeof(XState);

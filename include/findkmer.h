@@ -123,7 +123,12 @@ typedef struct {
                                  at finish from the caller's buffer instead of
                                  a copy the engine keeps: the caller leaves
                                  those bytes unchanged until fk_engine_finish
-                                 (or reset / destroy) returns.  0: copy (round 6) */
+                                 (or reset / destroy) returns.  0: copy (round 6).
+                                 Borrowed: a device feed that starts 16-B
+                                 aligned and has at least 32 bytes, except a
+                                 last segment of it shorter than 32 bytes;
+                                 copied: that tail, every host feed, and every
+                                 misaligned or shorter device feed */
     int32_t reserved[5];
 } fk_opts;
 

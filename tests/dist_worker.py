@@ -72,7 +72,7 @@ def main():
     # twice: the second pass reuses the engine, the buffer and the fast
     # path's scratch (stale rows from the first must not leak into it)
     shard = None if args.shard_table == "auto" else bool(int(args.shard_table))
-    for _ in range(2 if args.k < 16 else 1):   # (k = 16: a 16 GiB table a pass)
+    for _ in range(2 if args.k != 16 else 1):   # (k = 16: a 16 GiB table a pass; k >= 17: sparse, twice)
         eng.reset()
         res = fkdist.count_sharded(eng, dev.data_ptr() + halo, hi - lo, halo, buf, fast=bool(args.fast),
                                    native=bool(args.native), shard_table=shard, test_invalid=bool(args.test_invalid))

@@ -198,13 +198,32 @@ def test_shards_match_single(k, nshards):
     assert list(r_g.base_count) == list(r_o.base_count)
 
 
-@pytest.mark.parametrize("k", [1, 6, 11, 16])
+@pytest.mark.parametrize("k", [1, 6, 11, 13, 16, 20])
 def test_edge_sizes(k):
-    for data in [b"", b"A", b"ACGT" * 3, b">", b">abc", b"ACGT>x\n", b"\xff", b"AC\xffGT",
-                 b"A" * 65535, b"A" * 65536, b"A" * 65537, b"C" * (3 * 65536 + 17)]:
-        if k > 12:
-            continue
-        assert_same(data, k)
+    inputs = [b"", b"A", b"ACGT" * 3, b">", b">abc", b"ACGT>x\n", b"\xff", b"AC\xffGT",
+              b"A" * 65535, b"A" * 65536, b"A" * 65537, b"C" * (3 * 65536 + 17)]
+    if k == 16:
+        # 4^16 bins: the whole table is compared on the device (imported here:
+        # test_gpu_reuse imports this module), and one engine takes every
+        # input after a reset (a new 16 GiB engine for each costs 0.6 s)
+        import torch
+        from test_gpu_reuse import check, table_scratch
+        scratch = table_scratch(k)
+        with fk.Engine(k, want_nodes=True, collect_unknown=True) as e:
+            for data in inputs:
+                e.reset()
+                if data:
+                    e.feed(np.frombuffer(data, dtype=np.uint8).copy())
+                rc, r_g = e.finish(allow=(fk.FK_OK, fk.FK_E_EMPTY, fk.FK_E_UNTERMINATED_HEADER))
+                check(e, data, k, r_g, scratch=scratch)
+        del scratch
+        torch.cuda.empty_cache()
+        return
+    for data in inputs:
+        if k > 16:
+            assert_same_sparse(data, k)
+        else:
+            assert_same(data, k)
 
 
 def test_k16_dense_table():
