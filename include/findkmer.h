@@ -56,7 +56,13 @@ enum {
     FK_E_UNTERMINATED_HEADER = -7, /* input ends inside a '>' line: the ref
                                       spins forever in the loop at :1005 */
     FK_E_ROLLOVER = -8,         /* a trie counter would wrap: ref prints
-                                   COUNTER ROLLOVER and exits (:642-648) */
+                                   COUNTER ROLLOVER and exits (:642-648).
+                                   After a bin has wrapped, the table-derived
+                                   fields of fk_result (base_count, depth1,
+                                   distinct) describe the wrapped u32 table,
+                                   each wrap 2^32 short
+                                   (tests/test_gpu_counter_edge.py,
+                                   test_rollover_bin_wrap) */
     FK_E_STATE = -9,            /* API called out of order */
     FK_E_IO = -10,              /* host file I/O failed */
     FK_E_RCCL = -11,            /* a collective failed */
@@ -88,7 +94,8 @@ typedef struct {
 
 typedef struct {
     uint64_t base_count[4];   /* baseStatistics[b].Count, exact (the ref keeps
-                                 it in a u32 that wraps silently, :94) */
+                                 it in a u32 that wraps silently, :94) until
+                                 a bin wraps: see FK_E_ROLLOVER */
     uint64_t valid_bases;     /* baseCounter */
     uint64_t windows;         /* TotalNumSequencesN */
     uint64_t distinct;        /* k-mers with count >= 1 */
@@ -348,7 +355,8 @@ int  fk_engine_sparse(fk_engine *e, uint64_t *keys, uint32_t *counts, uint64_t c
  * memory -- a 10 GB input's table (~90 GB at k = 17) read piece by piece. */
 int  fk_engine_sparse_range(fk_engine *e, uint64_t key_lo, uint64_t key_hi, uint64_t *keys, uint32_t *counts,
                             uint64_t cap, uint64_t *n);
-/* The same into device buffers. */
+/* fk_engine_sparse into device buffers.  Both copy the whole table or
+ * nothing: with a buffer given and cap < *n they return FK_E_INVALID, *n set. */
 int  fk_engine_sparse_device(fk_engine *e, uint64_t *keys, uint32_t *counts, uint64_t cap, uint64_t *n);
 
 /* Multi-GPU merge of sparse tables (replaces the reduce of dense ones): the
